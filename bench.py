@@ -725,6 +725,38 @@ def measure_extras(hip, host, model, table, consts, a_cat, a_off, b_cat, b_off, 
     return out
 
 
+DUMP_BUDGET_BYTES = 63_000_000   # (64 MB in all with the .npy headers)
+DUMP_SEED = 20261015
+
+
+def dump_outputs(out_dir, fetched):
+    """--dump-outputs: the results a caller of the timed path receives (Batch.viterbi_fetch) for a fixed, seeded sample
+    of the pairs, as float32 / float64 .npy files of at most DUMP_BUDGET_BYTES in all: every pair when they fit, else
+    a prefix of a permutation seeded with DUMP_SEED, sized by the alignments' lengths (two builds that compute the
+    same results dump the same pairs).
+      pair_index  float64 [k]  the sampled pairs, ascending
+      scores      float32 [k]  Viterbi score of each
+      ops_len     float64 [k]  length of each alignment
+      ops_off     float64 [k]  where each alignment starts in the batch's concatenated op array
+      ops         float32 [sum ops_len]  the sampled pairs' ops (codes 0..2), concatenated in pair_index order"""
+    scores, ops, ops_off, ops_len = fetched
+    n = len(scores)
+    size = 4 * ops_len.astype(np.int64) + 4 + 3 * 8
+    if int(size.sum()) <= DUMP_BUDGET_BYTES:
+        idx = np.arange(n)
+    else:
+        perm = np.random.default_rng(DUMP_SEED).permutation(n)
+        idx = np.sort(perm[:int(np.searchsorted(np.cumsum(size[perm]), DUMP_BUDGET_BYTES, side="right"))])
+    off = ops_off[idx].astype(np.int64)
+    ln = ops_len[idx].astype(np.int64)
+    sel = np.concatenate([np.arange(o, o + l) for o, l in zip(off, ln)]) if len(idx) else np.zeros(0, np.int64)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, arr in (("pair_index", idx.astype(np.float64)), ("scores", scores[idx].astype(np.float32)),
+                      ("ops_len", ln.astype(np.float64)), ("ops_off", off.astype(np.float64)),
+                      ("ops", ops[sel].astype(np.float32))):
+        np.save(out_dir / f"{name}.npy", arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -744,7 +776,12 @@ def main():
     ap.add_argument("--streams", type=int, default=1, choices=[1, 2],
                     help="2: consecutive steps alternate between two resident copies of the shard on two library "
                          "streams, so the ragged end of one launch overlaps the start of the next (DESIGN.md 4.1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's batch) as DIR/<name>.npy "
+                         "(see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
 
@@ -838,6 +875,9 @@ def main():
         step()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # (untimed; before anything below launches the batch again)
+        last = slots[(state["i"] - 1) % len(slots)][1]
+        dump_outputs(Path(args.dump_outputs), last.viterbi_fetch())
     # per-kernel device times of the timed launches: HIP events the library recorded on its
     # own stream around each kernel (it keeps the last 64 launches)
     n_timed = max(1, min(args.steps // len(slots), 64))
