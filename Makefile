@@ -14,7 +14,7 @@ all: lib dist host oracle
 lib: $(BUILD)/libcoati_hip.so
 
 HIP_SRC = coati_amd/csrc/abi.hip coati_amd/csrc/plan.hip coati_amd/csrc/pipeline.hip coati_amd/csrc/sample_host.hip coati_amd/csrc/viterbi_ck.hip coati_amd/csrc/viterbi_l1.hip coati_amd/csrc/viterbi_lp.hip coati_amd/csrc/dp_generic.hip coati_amd/csrc/forward_l1.hip coati_amd/csrc/viterbi_k.hip coati_amd/csrc/forward_k.hip \
-          coati_amd/csrc/sampleback.hip
+          coati_amd/csrc/sampleback.hip coati_amd/csrc/viterbi_tri.hip
 $(BUILD)/libcoati_hip.so: $(HIP_SRC) coati_amd/csrc/viterbi_lp_block.inc coati_amd/csrc/abi_internal.hpp coati_amd/csrc/common.hpp coati_amd/csrc/viterbi_cell.hpp coati_amd/csrc/glibc_math.hpp include/coati_hip.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(HIP_SRC)
@@ -31,7 +31,7 @@ $(BUILD)/libcoati_hip_trace.so: $(HIP_SRC) coati_amd/csrc/viterbi_lp_block.inc c
 	$(HIPCC) $(HIPFLAGS) -DCOATI_FILL_TRACE -shared -o $@ $(HIP_SRC)
 
 HOST_SRC = coati_amd/host/model.cc coati_amd/host/seq.cc coati_amd/host/synth.cc coati_amd/host/io.cc \
-           coati_amd/host/align.cc coati_amd/host/cli.cc coati_amd/host/format.cc coati_amd/host/tree.cc coati_amd/host/insertions.cc coati_amd/host/msa.cc coati_amd/host/capi.cc
+           coati_amd/host/align.cc coati_amd/host/cli.cc coati_amd/host/format.cc coati_amd/host/tree.cc coati_amd/host/insertions.cc coati_amd/host/msa.cc coati_amd/host/triplet.cc coati_amd/host/capi.cc
 HOST_HDR = $(wildcard coati_amd/host/*.hpp) coati_amd/host/ecm_kosiol2007.inc
 CXX      ?= g++
 HOSTFLAGS = -std=c++17 -O2 -fPIC -pthread -ffp-contract=off -fno-fast-math -Wall -Wextra -Iinclude -Icoati_amd/host

@@ -57,7 +57,11 @@ EXPORTS = (
     "coati_hip_host_free",
     "coati_hip_debug_viterbi_flags",
     "coati_hip_debug_reload_env",
+    "coati_hip_triplet_model_create",
+    "coati_hip_triplet_model_destroy",
+    "coati_hip_triplet_align",
 )
+TRIPLET_CODON, TRIPLET_DNA = 0, 1  # coati_hip_triplet_model_create kinds
 
 
 class CoatiHipError(RuntimeError):
@@ -131,6 +135,11 @@ def load() -> C.CDLL:
         lib.coati_hip_host_alloc.argtypes = [u64, C.POINTER(vp)]
         lib.coati_hip_host_free.argtypes = [vp]
         lib.coati_hip_host_free.restype = None
+    if hasattr(lib, "coati_hip_triplet_align"):
+        lib.coati_hip_triplet_model_create.argtypes = [i32, vp, f32, f32, vp, f32, i32, C.POINTER(vp)]
+        lib.coati_hip_triplet_model_destroy.argtypes = [vp]
+        lib.coati_hip_triplet_model_destroy.restype = None
+        lib.coati_hip_triplet_align.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, u64, vp, vp]
     _lib = lib
     return lib
 
@@ -435,3 +444,69 @@ class Batch:
         if out.size:
             _check(load().coati_hip_debug_viterbi_flags(self._h, pair, _ptr(out), out.size))
         return out
+
+
+_NUC4 = np.full(256, 255, np.uint8)
+for _i, _c in enumerate("ACGT"):
+    _NUC4[ord(_c)] = _NUC4[ord(_c.lower())] = _i
+_NUC4[ord("U")] = _NUC4[ord("u")] = 3
+_NUC4[ord("N")] = _NUC4[ord("n")] = 4
+
+
+def triplet_encode(pairs):
+    """[(ancestor, descendant), ...] as strings -> (a_cat, a_off, b_cat, b_off) in coati_hip_triplet_align's codes
+    (A C G T/U -> 0..3, N -> 4; anything else 255, which the library rejects)."""
+    a = [np.frombuffer(x.encode(), np.uint8) for x, _ in pairs]
+    b = [np.frombuffer(y.encode(), np.uint8) for _, y in pairs]
+    a_off = np.zeros(len(pairs) + 1, np.uint64)
+    b_off = np.zeros(len(pairs) + 1, np.uint64)
+    a_off[1:] = np.cumsum([len(x) for x in a])
+    b_off[1:] = np.cumsum([len(y) for y in b])
+    a_cat = _NUC4[np.concatenate(a)] if a and a_off[-1] else np.zeros(0, np.uint8)
+    b_cat = _NUC4[np.concatenate(b)] if b and b_off[-1] else np.zeros(0, np.uint8)
+    return np.ascontiguousarray(a_cat), a_off, np.ascontiguousarray(b_cat), b_off
+
+
+class TripletModel:
+    """coati_hip_triplet_model_create: the FST aligner's models (align_fst.cc:fst_alignment) on the GPU.
+    cost: 61x61 (kind TRIPLET_CODON) or 4x4 (TRIPLET_DNA) arc weights; gap_open / gap_extend / pi / bc_error are
+    the probabilities indel() takes."""
+
+    def __init__(self, cost, gap_open=0.001, gap_extend=None, pi=(0.308, 0.185, 0.199, 0.308), bc_error=0.0001,
+                 device: int = 0):
+        cost = np.ascontiguousarray(cost, np.float32)
+        kind = TRIPLET_CODON if cost.size == 61 * 61 else TRIPLET_DNA
+        e = np.float32(1.0) - np.float32(1.0) / np.float32(6.0) if gap_extend is None else np.float32(gap_extend)
+        self._h = C.c_void_p()
+        self._cost = cost
+        _check(load().coati_hip_triplet_model_create(kind, _ptr(cost), np.float32(gap_open), e,
+                                                     _ptr(np.ascontiguousarray(pi, np.float32)), np.float32(bc_error),
+                                                     device, C.byref(self._h)))
+
+    def align(self, a_cat, a_off, b_cat, b_off):
+        """All pairs in one call: (scores, ops, ops_off, ops_len); pair p's columns are ops[ops_off[p]:+ops_len[p]]."""
+        n = len(a_off) - 1
+        a_cat = np.ascontiguousarray(a_cat, np.uint8)
+        b_cat = np.ascontiguousarray(b_cat, np.uint8)
+        a_off = np.ascontiguousarray(a_off, np.uint64)
+        b_off = np.ascontiguousarray(b_off, np.uint64)
+        cap = int(a_off[-1] - a_off[0] + b_off[-1] - b_off[0])
+        scores = np.zeros(n, np.float32)
+        ops = np.zeros(max(cap, 1), np.uint8)
+        ops_off = np.zeros(n, np.uint64)
+        ops_len = np.zeros(n, np.uint32)
+        _check(load().coati_hip_triplet_align(self._h, n, _ptr(a_cat), _ptr(a_off), _ptr(b_cat), _ptr(b_off), _ptr(scores),
+                                              _ptr(ops), cap, _ptr(ops_off), _ptr(ops_len)))
+        return scores, ops, ops_off, ops_len
+
+    def close(self):
+        if self._h:
+            load().coati_hip_triplet_model_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+

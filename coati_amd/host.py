@@ -87,6 +87,25 @@ def set_subst(model="mar-mg", br_len=0.0133, omega=0.2, pi=DEFAULT_PI, sigma=Non
     return out
 
 
+def triplet_model(model="tri-mg", br_len=0.0133, omega=0.2, pi=DEFAULT_PI, sigma=None):
+    """The triplet models' substitution weights (add_arc: -logf P) and the pi indel() sees: (cost, pi, codon) with
+    cost 61x61 for tri-mg / tri-ecm (codon True) and 4x4 for dna."""
+    cost = np.zeros(61 * 61, np.float32)
+    pi_out = np.zeros(4, np.float32)
+    codon = C.c_int(0)
+    sg = None if sigma is None else _f4(sigma)
+    _check(load().coati_host_triplet_model(model.encode(), C.c_float(np.float32(br_len)), C.c_float(np.float32(omega)),
+                                           _p(_f4(pi)), _p(sg), _p(cost), _p(pi_out), C.byref(codon)))
+    return (cost.reshape(61, 61) if codon.value else cost[:16].reshape(4, 4).copy()), pi_out, bool(codon.value)
+
+
+def dna_p(P) -> np.ndarray:
+    """dna()'s normalised 4x4 nucleotide matrix of a 61x61 codon P."""
+    out = np.zeros((4, 4), np.float32)
+    _check(load().coati_host_dna_p(_p(_f4(P)), _p(out)))
+    return out
+
+
 def encode(anc: str, des: str):
     ab, db = anc.encode(), des.encode()  # (buffers sized by BYTES: non-ASCII input must fail in the library, not overflow here)
     a = np.zeros(max(len(ab), 1), np.uint8)

@@ -42,6 +42,7 @@ class alignment_t {
     table_t subst_matrix;  // 183x15
     std::string output;
     bool score{false};
+    float bc_error{0.0001};  // NOLINT  base calling error rate (triplet models)
     AmbiguousNucs amb{AmbiguousNucs::SUM};
     MarginalSubst sub{MarginalSubst::SUM};
     int device{0};  // HIP device ordinal (not in the reference)

@@ -59,8 +59,10 @@ std::string usage(verb_t verb) {
                                                 "Usage: coati-alignpair [OPTIONS] input\n"
                                               : "coati sample - align two sequences and sample alignments\n"
                                                 "Usage: coati-sample [OPTIONS] input\n";
-    u += "  input                       Input file (FASTA/PHYLIP/JSON accepted)\n"
-         "  -m,--model TEXT             Substitution model (mar-mg mar-ecm)\n"
+    u += "  input                       Input file (FASTA/PHYLIP/JSON accepted)\n";
+    u += verb == verb_t::alignpair ? "  -m,--model TEXT             Substitution model (dna tri-mg tri-ecm mar-mg mar-ecm)\n"
+                                   : "  -m,--model TEXT             Substitution model (mar-mg mar-ecm)\n";
+    u += 
          "  --sub TEXT                  File with branch lengths and codon subst matrix\n"
          "  -t,--time FLOAT             Evolutionary time/branch length\n"
          "  -o,--output TEXT            Alignment output file\n"
@@ -77,6 +79,7 @@ std::string usage(verb_t verb) {
              "  -r,--ref TEXT               Name of reference sequence (default: 1st seq)\n"
              "  -v,--rev-ref                Use 2nd seq as reference (default: 1st seq)\n"
              "  -s,--score                  Score input alignment and exit\n"
+             "  -b,--base-error FLOAT       Base calling error rate (dna tri-mg tri-ecm)\n"
              "  --batch                     Input holds 2n sequences: align consecutive pairs (JSON array out)\n"
              "  --devices LIST              With --batch: one process per listed HIP device (e.g. 0,1,2,3), pairs sharded\n"
              "                              by DP cells, model broadcast and results gathered over RCCL\n";
@@ -140,7 +143,7 @@ args_t parse_arguments(verb_t verb, int argc, const char* const* argv) {
         } else if(a == "--device") {
             aln.device = std::atoi(need(i, a).c_str());
         } else if(a == "-b" || a == "--base-error") {
-            (void)positive_number(a, need(i, a));  // only used by the FST models
+            aln.bc_error = positive_number(a, need(i, a));  // only used by the triplet models
         } else if(verb == verb_t::alignpair && a == "--marginal-sub") {
             const std::string v = upper(need(i, a));
             if(v == "SUM" || v == "0")

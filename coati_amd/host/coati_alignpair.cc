@@ -1,5 +1,5 @@
 // coati-alignpair: the `coati alignpair` verb (src/coati-alignpair.cc:30-50) for the
-// marginal models, with the DP on an MI355X.
+// marginal and the triplet models, with the DP on an MI355X.
 #include <csignal>
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +16,7 @@
 #include "cli.hpp"
 #include "coati_hip.h"
 #include "io.hpp"
+#include "triplet.hpp"
 
 extern char** environ;
 
@@ -127,8 +128,11 @@ int main(int argc, char* argv[]) {
     }
     try {
         if(!args.aln.is_marginal()) {
-            // the triplet/FST models (tri-mg, tri-ecm, dna) are a different algorithm and not served here
-            throw std::invalid_argument("Mutation model unknown.");
+            // the triplet models (tri-mg, tri-ecm, dna): the reference's FST aligner (align_fst.cc), a DP on the GPU here
+            if(args.devices.size() > 1) throw std::invalid_argument("--devices with more than one device only supports marginal models.");
+            if(args.devices.size() == 1) args.aln.device = args.devices[0];
+            const bool ok = args.batch ? fst_alignment_batch(args.aln) : fst_alignment(args.aln);
+            return ok ? EXIT_SUCCESS : EXIT_FAILURE;
         }
         if(args.dist_rank >= 0)  // a child of the --devices launcher below: rank dist_rank on --device
             return marg_alignment_batch_dist(args.aln, args.dist_rank, args.dist_world, args.dist_id) ? EXIT_SUCCESS : EXIT_FAILURE;

@@ -43,5 +43,8 @@ int coati_hip_viterbi_batch(coati_hip_model_t*, uint64_t, const uint8_t*, const 
 int coati_hip_shard_bounds(uint64_t, const uint64_t*, const uint64_t*, int, uint64_t*) { return kNo; }
 int coati_hip_host_alloc(uint64_t, void** out) { if(out) *out = nullptr; return kNo; }
 void coati_hip_host_free(void*) {}
+int coati_hip_triplet_model_create(int, const float*, float, float, const float*, float, int, coati_hip_triplet_model_t** out) { if(out) *out = nullptr; return kNo; }
+void coati_hip_triplet_model_destroy(coati_hip_triplet_model_t*) {}
+int coati_hip_triplet_align(coati_hip_triplet_model_t*, uint64_t, const uint8_t*, const uint64_t*, const uint8_t*, const uint64_t*, float*, uint8_t*, uint64_t, uint64_t*, uint32_t*) { return kNo; }
 int coati_hip_debug_viterbi_flags(coati_hip_batch_t*, uint64_t, uint8_t*, uint64_t) { return kNo; }
 }

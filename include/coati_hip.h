@@ -301,6 +301,38 @@ void coati_hip_debug_reload_env(void);
 int coati_hip_debug_viterbi_flags(coati_hip_batch_t* batch, uint64_t pair, uint8_t* out,
                                   uint64_t capacity);
 
+/* ---- triplet models (tri-mg, tri-ecm, dna) -------------------------------- *
+ * Replace the reference's FST aligner, src/lib/align_fst.cc:fst_alignment: the composition
+ * ancestor FSA o (mutation FST o indel FST) o descendant FSA and its ShortestPath, for the models
+ * built by mg94() / ecm() / dna() / indel() (src/lib/mutation_fst.cc, mutation_ecm.cc:194-218).
+ * Here the same minimum is found by a tropical-semiring DP (csrc/viterbi_tri.hip).
+ *
+ * kind COATI_HIP_TRIPLET_CODON: cost_table is 61x61 fp32, row-major, cost_table[c*61+c'] = the
+ *   weight of the mg94()/ecm() path that reads sense codon c and writes sense codon c'
+ *   (add_arc: -logf(P), 0 where P == 1, INT_MAX where P == 0).
+ * kind COATI_HIP_TRIPLET_DNA: cost_table is 4x4, the weights of dna()'s arcs (-logf(dna_p)).
+ * gap_open, gap_extend, pi[4], bc_error: the PROBABILITIES indel() takes; the library turns them into
+ *   arc weights with add_arc's rule.  0 < gap_open, gap_extend < 1, 0 < bc_error <= 1/3, 0 <= pi <= 1. */
+enum { COATI_HIP_TRIPLET_CODON = 0, COATI_HIP_TRIPLET_DNA = 1 };
+typedef struct coati_hip_triplet_model coati_hip_triplet_model_t;
+int coati_hip_triplet_model_create(int kind, const float* cost_table, float gap_open, float gap_extend,
+                                   const float pi[4], float bc_error, int device,
+                                   coati_hip_triplet_model_t** out);
+void coati_hip_triplet_model_destroy(coati_hip_triplet_model_t* model);
+/* Align n_pairs pairs (align_fst.cc:fst_alignment, batched: one launch per chunk of pairs whose
+ * traceback decisions fit a device budget; a pair larger than the budget is a chunk of its own).
+ * a_cat: ancestor nucleotides 0..3 (A C G T), length a multiple of 3, no stop codon (TAA TAG TGA);
+ * b_cat: descendant 0..3 (A C G T) or 4 (N).  Pair p = a_cat[a_off[p]..a_off[p+1]),
+ * b_cat[b_off[p]..b_off[p+1]).
+ * Out: scores[p] = the shortest distance (fp32); the alignment columns (COATI_HIP_OP_*) of pair p
+ * are ops[ops_off[p] .. ops_off[p] + ops_len[p]), inside pair p's slot of len_a + len_b bytes
+ * (slots back to back in pair order); ops_cap >= sum of len_a + len_b.
+ * Between the optimal alignments of equal cost the DP keeps one by a fixed rule. */
+int coati_hip_triplet_align(coati_hip_triplet_model_t* model, uint64_t n_pairs, const uint8_t* a_cat,
+                            const uint64_t* a_off, const uint8_t* b_cat, const uint64_t* b_off,
+                            float* scores, uint8_t* ops, uint64_t ops_cap, uint64_t* ops_off,
+                            uint32_t* ops_len);
+
 #ifdef __cplusplus
 }
 #endif
