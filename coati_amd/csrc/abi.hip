@@ -110,6 +110,7 @@ const EnvOptions* read_env() {
         const long x = std::atol(e);
         o->ck_band = x <= 0 ? kCkBandOff : static_cast<uint32_t>(x);
     }
+    if(const long long x = num("COATI_HIP_CK_ORIENT", 1); x >= 0 && x <= 2) o->ck_orient = static_cast<uint32_t>(x);
     o->ck_debug = static_cast<uint32_t>(num("COATI_HIP_CK_DEBUG", 0));
     o->ck_walk_items = static_cast<int>(num("COATI_HIP_CK_WALK_ITEMS", -1));
     o->ck_fuse = static_cast<int>(num("COATI_HIP_CK_FUSE", -1));
@@ -148,6 +149,7 @@ const EnvOptions& env_options() {
 }
 bool forward_fast_math() { return env_options().forward_fast; }
 uint32_t ck_band_setting() { return env_options().ck_band; }
+uint32_t ck_orient_setting() { return env_options().ck_orient; }
 }  // namespace coati_hip_detail
 
 extern "C" void coati_hip_debug_reload_env(void) {
@@ -335,6 +337,7 @@ int coati_hip_model_create_tables(const float* table, uint32_t n_tables, float n
     m->device = device;
     m->gap_len = gap_len;
     m->ck_band = ck_band_setting();
+    m->ck_orient = ck_orient_setting();
     m->n_tables = n_tables;
     m->forward_mode.store(forward_fast_math() ? COATI_HIP_FORWARD_TOLERANCE : COATI_HIP_FORWARD_EXACT);  // (the environment's default)
     m->k = GapConsts{no_gap, gap_stop, gap_open, gap_extend};
@@ -464,6 +467,11 @@ int coati_hip_model_set_option(coati_hip_model_t* model, int option, int64_t val
     if(option == COATI_HIP_OPT_CK_BAND) {
         if(value < 0 || value > 0x7fffffff) return fail(COATI_HIP_EINVAL, "model_set_option: band of %lld steps", static_cast<long long>(value));
         model->ck_band = value == 0 ? kCkBandOff : static_cast<uint32_t>(value);
+        return COATI_HIP_OK;
+    }
+    if(option == COATI_HIP_OPT_CK_ORIENT) {
+        if(value < 0 || value > 2) return fail(COATI_HIP_EINVAL, "model_set_option: orientation mode %lld", static_cast<long long>(value));
+        model->ck_orient = static_cast<uint32_t>(value);
         return COATI_HIP_OK;
     }
     if(option == COATI_HIP_OPT_FORWARD_MODE) {

@@ -78,7 +78,30 @@ struct PairDesc {
     // viterbi_ck: the pair's (single) strip is cut into this many ROW parts, each its own work item, continued by
     // whichever wavefront takes the next part (0 or 1: not cut).  Finer items for the ragged end of a launch.
     uint8_t v_parts;
+    // viterbi_ck: 1 = the pair is filled TRANSPOSED -- wavefront steps along the descendant, the 64 x W lane columns along the
+    // ancestor (ck_fill_frame).  Only where the transposed pair is one strip; v_strips / v_wmain / v_wlast / v_parts and the
+    // pair's checkpoint storage describe the transposed fill.
+    uint8_t v_orient;
 };
+// The pair as viterbi_ck's fill sees it: itself, or (PairDesc::v_orient) its transpose -- extents and sequence offsets swapped
+// (the caller swaps the two code arrays the offsets index).  The
+// cell is the same; which of its values a lane carries from step to step and which it chains to the next column trade places
+// (viterbi_ck.hip, kT), and the walk maps its matrix coordinates into this frame.
+__host__ __device__ inline PairDesc ck_fill_frame(const PairDesc& d) {
+    PairDesc f = d;
+    if(d.v_orient != 0) {
+        f.la = d.lb, f.lb = d.la;
+        f.a_off = d.b_off, f.b_off = d.a_off;
+    }
+    return f;
+}
+// COATI_HIP_OPT_CK_ORIENT: 0 = never transpose, 1 = where it lowers the strip count or (one strip either way) the steps,
+// 2 = every pair that is one strip transposed (tests)
+__host__ __device__ inline bool ck_orient_transposed(uint32_t mode, uint32_t strips_n, uint32_t strips_t, uint32_t la, uint32_t lb) {
+    if(strips_t != 1u || mode == 0u) return false;
+    if(mode == 2u) return true;
+    return strips_n > 1u || lb < la;
+}
 // PairDesc::v_parts: the number of row parts in the low four bits; bit 7 = TAPERED parts (below); bits 4-6 = how many
 // 64-step chunks the LAST part is shorter than an equal split would make it (round 5: the wavefront of the last part also
 // walks the pair -- ~0.17 ms, two chunks' worth -- and the items at the end of the queue are the last parts)
@@ -603,6 +626,7 @@ struct EnvOptions {
     int lp_blocks_per_cu = 0;        // COATI_HIP_LP_BLOCKS_PER_CU
     long long tail_pairs = -1;       // COATI_HIP_TAIL_PAIRS (-1: the planner's rule)
     uint32_t ck_band = 64;           // COATI_HIP_CK_BAND: default of COATI_HIP_OPT_CK_BAND (0 -> kCkBandOff)
+    uint32_t ck_orient = 1;          // COATI_HIP_CK_ORIENT: default of COATI_HIP_OPT_CK_ORIENT (0 never, 1 auto, 2 every pair that can)
     uint32_t ck_debug = 0;           // COATI_HIP_CK_DEBUG: bit 0 fill only, bit 1 traceback statistics
     bool ck_split_set = false;       // COATI_HIP_CK_SPLIT="pairs,parts[,t]"
     uint64_t ck_split_pairs = 0, ck_split_parts = 3;
@@ -727,6 +751,7 @@ volatile uint32_t* ck_stream_host_done_flag(void* host, int slot);
 hipError_t launch_viterbi_ck_stream(const float* table, GapConsts k, bool shared_tab, void* ctl, const void* host_words, uint32_t* wave_ck,
                                     uint64_t wave_slot_dwords, uint32_t* wave_scratch, uint32_t band, hipStream_t stream);
 uint32_t ck_band_setting();  // the default half width of the kept checkpoint band (COATI_HIP_CK_BAND, else 64 steps)
+uint32_t ck_orient_setting();  // the default of COATI_HIP_OPT_CK_ORIENT (COATI_HIP_CK_ORIENT, else 1 = auto)
 hipError_t launch_ck_all_flags(const BatchDeviceView& v, uint32_t pair, uint32_t* scratch, uint32_t n_waves, uint8_t* out,
                                hipStream_t stream);
 hipError_t launch_dp_generic(const BatchDeviceView& v, bool forward, hipStream_t stream);

@@ -350,6 +350,11 @@ int batch_create_impl(coati_hip_model_t* model, uint64_t n_pairs, const uint8_t*
         if(items_main < 1024) k_main = k_narrow;
     }
     bool all_narrow = plan_k;
+    // viterbi_ck's transposed fills (PairDesc::v_orient, COATI_HIP_OPT_CK_ORIENT): batches of their own only -- not the chunks
+    // of a pipelined or streamed call (pipeline.hip sizes their workspaces by the ancestor's length), the debug export or a
+    // debug re-run of one pair
+    const uint32_t orient_mode = (b->ck && (opts == nullptr || (opts->arena == nullptr && opts->wave_slot_dwords == 0 && !opts->ck_per_pair && opts->force_w_main == 0)))
+                                     ? model->ck_orient : 0u;
     for(uint64_t p = 0; p < n_pairs; ++p) {
         PairDesc& d = b->desc[p];
         const uint64_t la = d.la;
@@ -357,8 +362,16 @@ int batch_create_impl(coati_hip_model_t* model, uint64_t n_pairs, const uint8_t*
         uint32_t w_main_q = w_main_p;  // columns per lane of every strip but the last
         uint32_t ns = 1, wl = w_main_p;
         d.v_compact = 0;
+        d.v_orient = 0;
         if(plan_l1) {
             if(d.la > 0 && d.lb > 0) viterbi_strip_plan(d.lb, w_main_p, ns, wl);
+            if(orient_mode != 0u && d.la > 0 && d.lb > 0) {
+                // the transposed fill: steps along the descendant, lane columns along the ancestor (viterbi_ck.hip, kT) -- where
+                // that makes the pair one strip instead of several, or (one strip either way) takes lb + 63 steps instead of la + 63
+                uint32_t ns_t = 1, wl_t = w_main_p;
+                viterbi_strip_plan(d.la, w_main_p, ns_t, wl_t);
+                if(ck_orient_transposed(orient_mode, ns, ns_t, d.la, d.lb)) d.v_orient = 1, ns = ns_t, wl = wl_t;
+            }
         } else if(plan_k) {
             d.v_compact = static_cast<uint32_t>(L);
             const uint32_t cols_b = static_cast<uint32_t>(d.lb / L), narrow = k_narrow;
@@ -381,7 +394,7 @@ int batch_create_impl(coati_hip_model_t* model, uint64_t n_pairs, const uint8_t*
         d.bnd_off = b->bnd_floats;
         if(d.la > 0 && d.lb > 0)
             b->flag_dwords += plan_k  ? ns * compact_strip_dwords(d.la, static_cast<uint32_t>(L))
-                              : b->ck ? (ns - 1) * ck_strip_dwords(d.la, w_main_p) + ck_strip_dwords(d.la, wl)
+                              : b->ck ? (ns - 1) * ck_strip_dwords(d.la, w_main_p) + ck_strip_dwords(d.v_orient ? d.lb : d.la, wl)
                                       : (ns - 1) * strip_dwords(d.la, w_main_p) + strip_dwords(d.la, wl);
         // strip-boundary arrays, 128-byte aligned so that no two waves ever share a cache line:
         // viterbi_l1 one 2(la+1) array per boundary of its plan, forward_l1 one 3(la+1) array per
@@ -436,12 +449,12 @@ int batch_create_impl(coati_hip_model_t* model, uint64_t n_pairs, const uint8_t*
                 d.flags_off = at;
             } else if(d.v_parts >= 2) {
                 d.flags_off = at;
-                at += ck_strip_dwords(d.la, d.v_wlast) + kCkPartStateDwords;
-            } else if(d.v_strips == 1 && ck_strip_dwords(d.la, d.v_wlast) <= opts->wave_slot_dwords) {
+                at += ck_strip_dwords(ck_fill_frame(d).la, d.v_wlast) + kCkPartStateDwords;
+            } else if(d.v_strips == 1 && ck_strip_dwords(ck_fill_frame(d).la, d.v_wlast) <= opts->wave_slot_dwords) {
                 d.flags_off = kCkWaveSlot;
             } else {
                 d.flags_off = at;
-                at += (d.v_strips - 1) * ck_strip_dwords(d.la, d.v_wmain) + ck_strip_dwords(d.la, d.v_wlast);
+                at += (d.v_strips - 1) * ck_strip_dwords(d.la, d.v_wmain) + ck_strip_dwords(ck_fill_frame(d).la, d.v_wlast);
             }
         }
         b->flag_dwords = at;
@@ -451,7 +464,8 @@ int batch_create_impl(coati_hip_model_t* model, uint64_t n_pairs, const uint8_t*
     } else if(b->ck && !env.ck_per_pair) {
         constexpr uint64_t kSlotCap = 1ull << 20;  // dwords (4 MB)
         uint64_t slot = 0, per_pair_total = 0;
-        auto need_of = [&](const PairDesc& d) { return d.la > 0 && d.lb > 0 ? ck_strip_dwords(d.la, d.v_wlast) : 0; };
+        // (the checkpoints of the pair's fill: a transposed pair's steps run along the descendant)
+        auto need_of = [&](const PairDesc& d) { return d.la > 0 && d.lb > 0 ? ck_strip_dwords(ck_fill_frame(d).la, d.v_wlast) : 0; };
         for(uint64_t p = 0; p < n_pairs; ++p) {
             const PairDesc& d = b->desc[p];
             if(d.v_strips != 1) continue;
@@ -506,8 +520,9 @@ int batch_create_impl(coati_hip_model_t* model, uint64_t n_pairs, const uint8_t*
         std::vector<uint32_t> cut;  // in LPT order
         for(uint64_t q = n_pairs - split_pairs; q < n_pairs; ++q) {
             PairDesc& d = b->desc[order[q]];
+            const PairDesc f = ck_fill_frame(d);  // (the fill's extents: a transposed pair's rows are its descendant)
             // (every part at least a 64-step chunk, two on average; narrow last strips and multi-strip pairs stay whole)
-            const uint32_t nsteps = d.la + (std::min<uint32_t>(kStrip, d.lb) + kW - 1) / kW - 1;
+            const uint32_t nsteps = f.la + (std::min<uint32_t>(kStrip, f.lb) + kW - 1) / kW - 1;
             if(d.la > 0 && d.lb > 0 && d.v_strips == 1 && d.v_wlast == kW && need_of(d) <= kSlotCap &&
                ck_parts_fit(nsteps, static_cast<uint32_t>(parts), taper)) {
                 // The wavefront of a pair's LAST part also walks the pair (a 1 kb pair: ~0.17 ms, two to three chunks' worth), and
@@ -516,7 +531,7 @@ int batch_create_impl(coati_hip_model_t* model, uint64_t n_pairs, const uint8_t*
                 // chunks).  Only where every part keeps at least two chunks.
                 const uint32_t chunks = (nsteps + 63u) / 64u;
                 // (with the traceback as an item of its own -- COATI_HIP_CK_WALK_ITEMS -- the last part is a part like the others)
-                const uint32_t want = walk_items ? 0u : env.ck_split_set ? short_last : std::min<uint32_t>(7u, (3u * d.lb + 500u) / 1000u);
+                const uint32_t want = walk_items ? 0u : env.ck_split_set ? short_last : std::min<uint32_t>(7u, (3u * f.lb + 500u) / 1000u);
                 const uint32_t sl = taper ? 0u : ck_fit_short_last(chunks, static_cast<uint32_t>(parts), want);  // (every part keeps >= 2 chunks of the REAL cut)
                 d.v_parts = static_cast<uint8_t>(parts | (taper ? kCkPartsTaper : 0u) | (sl << 4));
                 cut.push_back(order[q]);
@@ -542,12 +557,12 @@ int batch_create_impl(coati_hip_model_t* model, uint64_t n_pairs, const uint8_t*
                 }
                 if(d.v_parts >= 2) {
                     d.flags_off = at;
-                    at += ck_strip_dwords(d.la, d.v_wlast) + kCkPartStateDwords;
+                    at += ck_strip_dwords(ck_fill_frame(d).la, d.v_wlast) + kCkPartStateDwords;
                 } else if(use_slots && d.v_strips == 1 && need_of(d) <= kSlotCap) {
                     d.flags_off = kCkWaveSlot;
                 } else {
                     d.flags_off = at;
-                    at += (d.v_strips - 1) * ck_strip_dwords(d.la, d.v_wmain) + ck_strip_dwords(d.la, d.v_wlast);
+                    at += (d.v_strips - 1) * ck_strip_dwords(d.la, d.v_wmain) + ck_strip_dwords(ck_fill_frame(d).la, d.v_wlast);
                 }
             }
             b->flag_dwords = at;

@@ -84,13 +84,18 @@ struct LaneState {
     "v_alignbit_b32 %[aA], %[aA], %[t5], 31\n\t" /* S  M2                                */ \
     "v_alignbit_b32 %[aB], %[aB], %[t7], 31"    /* S  D1                                   */
 
-template <int C, int W>
+// kT (viterbi_ck's transposed fill: the lane's W columns are matrix ROWS, its steps matrix columns): the lane carries the I
+// value of each of its rows from step to step in st.Y and chains the D value from row to row in `zl` -- the same block on the
+// same operands, bound the other way round; the decisions are those of the matrix cell either way.
+template <int C, int W, bool kT = false>
 __device__ __forceinline__ void cell_l1(const GapVec& k, LaneState<W>& st, float& diag, float& zl, float& pend,
                                         float& s, uint32_t lds_next_row, uint32_t boff) {
     float x_new, t0, t1, t2, t3, t4, t5, t6, t7, t8, t9, t10;
     uint32_t addr;
+    float& d_in = kT ? zl : st.Y[C];  // D input -> D of the cell below
+    float& i_in = kT ? st.Y[C] : zl;  // I input -> I of the cell to the right
 #define COATI_CELL_OPERANDS                                                                              \
-    : [x] "=&v"(x_new), [y] "+v"(st.Y[C]), [zl] "+v"(zl), [pend] "+v"(pend), [aA] "+v"(st.acc[ACC_A]),   \
+    : [x] "=&v"(x_new), [y] "+v"(d_in), [zl] "+v"(i_in), [pend] "+v"(pend), [aA] "+v"(st.acc[ACC_A]),   \
       [aB] "+v"(st.acc[ACC_B]), [aC] "+v"(st.acc[ACC_C]), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), \
       [t3] "=&v"(t3), [t4] "=&v"(t4), [t5] "=&v"(t5), [t6] "=&v"(t6), [t7] "=&v"(t7), [t8] "=&v"(t8),     \
       [t9] "=&v"(t9), [t10] "=&v"(t10), [addr] "=&v"(addr)                                                \
@@ -108,13 +113,13 @@ __device__ __forceinline__ void cell_l1(const GapVec& k, LaneState<W>& st, float
     s = *reinterpret_cast<const __attribute__((address_space(3))) float*>(addr);
 }
 
-template <int W, int... C>
+template <int W, bool kT = false, int... C>
 __device__ __forceinline__ void row_l1(const GapVec& k, LaneState<W>& st, float diag, float zl,
                                        float (&s)[W], uint32_t lds_next_row, const uint32_t (&boff)[W],
                                        std::integer_sequence<int, C...>) {
     st.xlast_old = st.X[W - 1];
     float pend = 0.0f;
-    (cell_l1<C, W>(k, st, diag, zl, pend, s[C], lds_next_row, boff[C]), ...);
+    (cell_l1<C, W, kT>(k, st, diag, zl, pend, s[C], lds_next_row, boff[C]), ...);
     asm volatile("v_alignbit_b32 %0, %0, %1, 31" : "+v"(st.acc[ACC_B]) : "v"(pend));  // D2 of the last column
     st.zlast = zl;
 }

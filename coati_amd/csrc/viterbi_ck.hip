@@ -53,10 +53,51 @@ namespace {
 template <int W>
 struct CkLane {
     float X[W];  // max((M+ng)+ng, D+gs, (I+gs)+ng): feeds M of the next diagonal cell
-    float Y[W];  // max((M+ng)+go, D+ge, (I+gs)+go): the D value of the cell below
+    float Y[W];  // max((M+ng)+go, D+ge, (I+gs)+go): the D value of the cell below (kT: max(M+go, I+ge), the I value of the next step)
     float xlast_old;  // X[W-1] of the row before: the right neighbour's diagonal input
-    float zlast;      // max(M+go, I+ge) of column W-1: the right neighbour's I value
+    float zlast;      // max(M+go, I+ge) of column W-1: the right neighbour's I value (kT: its D value)
 };
+
+// TRANSPOSED FILLS (round 7, kT; PairDesc::v_orient).  The fill runs over ck_fill_frame(pair): steps along the descendant, the
+// lane columns along the ancestor.  The cell is the same 15 instructions on the same operands; what a lane carries per column
+// from step to step is then the I value (Z) and what it chains to its next column -- and across lanes by the shift -- the D
+// value (Y): cell_lean binds the two the other way round.  The score of a cell is tab[ancestor row][descendant column] either
+// way: the per-step part of its LDS address is the descendant's code * 4, the per-column part the ancestor's row offset
+// (ck_tab_mul).  Checkpoints, bands, row parts and the walk's tiles are those of the transposed matrix; the walk maps its
+// matrix coordinates into it (ck_walk_pair).
+// byte offset of a code in the LDS table: the fill's rows (kRow) and its columns -- ancestor rows and descendant columns of the
+// table, or transposed the other way round
+template <bool kT, bool kRow>
+__device__ __forceinline__ constexpr uint32_t ck_tab_mul() {
+    return (kT != kRow) ? kTabStride * 4u : 4u;
+}
+// the state a lane column starts from: the fill's margin row -- matrix row 0 (align_pair.cc:88-90: M = D = lowest, I = go +
+// ge*float(j-1)) at fill column q = j - 1, or transposed matrix column 0 (align_pair.cc:82-86: M = I = lowest, D = (ng+go) +
+// ge*float(i-1)) at q = i - 1, whose X is D + gs and whose I value for column 1 is lowest
+template <bool kT>
+__device__ __forceinline__ void ck_margin_state(const GapConsts& k, uint32_t q, float& x, float& y) {
+    if constexpr(kT) {
+        x = ((k.ng + k.go) + k.ge * static_cast<float>(q)) + k.gs;
+        y = kLowest;
+    } else {
+        const float im = k.go + k.ge * static_cast<float>(q);
+        const float i1 = im + k.gs;
+        x = i1 + k.ng;
+        y = i1 + k.go;
+    }
+}
+// what lane 0 of the pair's first strip takes from the left for fill row r: the fill's margin column -- matrix column 0 (diagonal
+// X(r, 0), and the I value of (r + 1, 0): lowest), or transposed matrix row 0 (diagonal X(0, r), and the D value Y(0, r + 1))
+template <bool kT>
+__device__ __forceinline__ void ck_margin_left(const GapConsts& k, uint32_t r, float& bx, float& bz) {
+    if constexpr(kT) {
+        bx = r == 0 ? (0.0f + k.ng) + k.ng : ((k.go + k.ge * static_cast<float>(r - 1)) + k.gs) + k.ng;
+        bz = ((k.go + k.ge * static_cast<float>(r)) + k.gs) + k.go;
+    } else {
+        bx = r == 0 ? (0.0f + k.ng) + k.ng : ((k.ng + k.go) + k.ge * static_cast<float>(r - 1)) + k.gs;
+        bz = kLowest;
+    }
+}
 
 // The recurrence of one cell (align_pair.cc:97-124 with look_back = 1; the algebra is in
 // viterbi_cell.hpp / DESIGN.md §2): 11 v_add_f32, the LDS address of this column's score for the
@@ -81,12 +122,14 @@ struct CkLane {
 // (Five temporaries: the register-only replay of the cell, tools/ubench/gen_cell_pk.py, runs at the
 // same rate whatever the order of the 15 instructions, so the order is the one with the shortest
 // live ranges.  `s` is consumed by the first instruction and then carries the LDS address.)
-template <int C, int W>
+template <int C, int W, bool kT>
 __device__ __forceinline__ void cell_lean(const GapVec& k, CkLane<W>& st, float& diag, float& zl, float& s,
                                           uint32_t lds_next_row, uint32_t boff) {
     float x_new, t0, t1, t2, t3, t4;
+    float& d_in = kT ? zl : st.Y[C];  // D input -> D of the cell below
+    float& i_in = kT ? st.Y[C] : zl;  // I input -> I of the cell to the right
     asm volatile(COATI_CELL_LEAN
-                 : [x] "=&v"(x_new), [y] "+v"(st.Y[C]), [zl] "+v"(zl), [s] "+v"(s), [t0] "=&v"(t0), [t1] "=&v"(t1),
+                 : [x] "=&v"(x_new), [y] "+v"(d_in), [zl] "+v"(i_in), [s] "+v"(s), [t0] "=&v"(t0), [t1] "=&v"(t1),
                    [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4)
                  : [diag] "v"(diag), [lds] "v"(lds_next_row), [boff] "v"(boff), [ng] "v"(k.ng), [gs] "v"(k.gs),
                    [go] "v"(k.go), [ge] "v"(k.ge));
@@ -97,12 +140,12 @@ __device__ __forceinline__ void cell_lean(const GapVec& k, CkLane<W>& st, float&
     s = *reinterpret_cast<const volatile __attribute__((address_space(3))) float*>(__builtin_bit_cast(uint32_t, s));
 }
 
-template <int W, int... C>
+template <int W, bool kT, int... C>
 __device__ __forceinline__ void row_lean(const GapVec& k, CkLane<W>& st, float diag, float zl, float (&s)[W],
                                          uint32_t lds_next_row, const uint32_t (&boff)[W],
                                          std::integer_sequence<int, C...>) {
     st.xlast_old = st.X[W - 1];
-    (cell_lean<C, W>(k, st, diag, zl, s[C], lds_next_row, boff[C]), ...);
+    (cell_lean<C, W, kT>(k, st, diag, zl, s[C], lds_next_row, boff[C]), ...);
     st.zlast = zl;
 }
 
@@ -222,7 +265,7 @@ __device__ __forceinline__ void store_rowck(const CkChunkMem& mem, int lane, con
 // whatever it holds (never looked at), and at step l it takes the state of the margin row.  ONE
 // instantiation serves every chunk: a separate start-up copy of the loop (as viterbi_l1.hip has)
 // cost ~50 VGPRs here and with them the fourth wavefront per SIMD.
-template <int W, bool kSub, bool kSingle, bool kThrough>
+template <int W, bool kSub, bool kSingle, bool kThrough, bool kT>
 __device__ __forceinline__ void ck_step(const CkCtx& cx, const CkChunkMem& mem, CkLane<W>& st, uint32_t& arow,
                                         float (&s)[W], const uint32_t (&boff)[W], uint32_t kbase, uint32_t kk,
                                         uint32_t a_chunk, float bx, float bz, uint32_t colin_voff, uint32_t colin_band_soff, uint32_t colin_step_shift) {
@@ -233,17 +276,11 @@ __device__ __forceinline__ void ck_step(const CkCtx& cx, const CkChunkMem& mem, 
     // wavefront that is alone on its SIMD ~130 cycles)
     // (kSub only: with four wavefronts per SIMD the single-strip fill measured 1 % slower that way)
     if((kSub ? __builtin_expect(kbase == 0, 0) : static_cast<long>(kbase == 0)) && kk == static_cast<uint32_t>(lane)) {
-        // This lane starts now: state of the margin row (matrix row 0, align_pair.cc:88-90):
-        // M = D = lowest, I = go + ge*float(j-1).
+        // This lane starts now: state of the margin row (ck_margin_state)
         uint32_t bj0 = cx.col0 + lane * W;
         asm volatile("" : "+v"(bj0));  // compute in place (hoisted out of the loop these 2W values get spilled)
 #pragma unroll
-        for(int c = 0; c < W; ++c) {
-            const float im = k.go + k.ge * static_cast<float>(bj0 + c);
-            const float i1 = im + k.gs;
-            st.X[c] = i1 + k.ng;
-            st.Y[c] = i1 + k.go;
-        }
+        for(int c = 0; c < W; ++c) ck_margin_state<kT>(k, bj0 + c, st.X[c], st.Y[c]);
     }
     // ---- hand-off from the left neighbour (full exec)
     // (kSub: bx / bz hold the 16 rows of the current sub-block in lanes 0-15, else the chunk's 64 rows)
@@ -258,7 +295,7 @@ __device__ __forceinline__ void ck_step(const CkCtx& cx, const CkChunkMem& mem, 
     __builtin_amdgcn_raw_buffer_store_b64(u32x2{fbits(diag), fbits(zl)}, mem.colin, colin_voff, colin_band_soff + (kk << colin_step_shift),
                                           kThrough ? kAuxAgent : kAuxPlain);
     // ---- the W cells (and the LDS gather for the next step)
-    row_lean<W>(cx.kv, st, diag, zl, s, cx.lds_tab + arow_next, boff, std::make_integer_sequence<int, W>{});
+    row_lean<W, kT>(cx.kv, st, diag, zl, s, cx.lds_tab + arow_next, boff, std::make_integer_sequence<int, W>{});
     arow = arow_next;
     // lane 63 just did body row kstep - 63: its last column is the next strip's boundary
     // (kSingle -- the pair has one strip, known where the call is made: nothing here)
@@ -283,7 +320,7 @@ __device__ __forceinline__ void ck_step(const CkCtx& cx, const CkChunkMem& mem, 
 // strip loads the 16 rows of its next sub-block past the L2 until none is the pattern.  A strip then follows its
 // neighbour at 63 (the skew of the 64 lanes) + 16 + a round trip steps instead of 63 + 64 + a drain + a poll + an
 // L2 invalidate (viterbi_l1 / viterbi_lp do the same).  Returns false if values never arrived.
-template <int W, bool kSub, bool kSingle, bool kThrough>
+template <int W, bool kSub, bool kSingle, bool kThrough, bool kT>
 __device__ __forceinline__ bool ck_chunk(const CkCtx& cx, const CkChunkMem& mem, CkLane<W>& st, uint32_t& arow,
                                          float (&s)[W], const uint32_t (&boff)[W], uint32_t kbase, uint32_t a_chunk,
                                          float bx, float bz, unsigned long long& pre) {
@@ -352,7 +389,7 @@ __device__ __forceinline__ bool ck_chunk(const CkCtx& cx, const CkChunkMem& mem,
                 for(uint32_t u = 0; u < kCkRows; ++u) {
                     if(u == kCkPrefetchAt && !cx.first_strip && row + kCkRows < cx.la)  // (W = 16: `pre` stays "not there", the sub-block asks when it begins)
                         pre = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(cx.bnd_in) + row + kCkRows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ck_step<W, kSub, kSingle, kThrough>(cx, mem, st, arow, s, boff, kbase, kb + u, a_chunk, bx, bz, colin_voff, colin_band_soff, colin_step_shift);
+                    ck_step<W, kSub, kSingle, kThrough, kT>(cx, mem, st, arow, s, boff, kbase, kb + u, a_chunk, bx, bz, colin_voff, colin_band_soff, colin_step_shift);
                 }
                 continue;
             }
@@ -362,10 +399,10 @@ __device__ __forceinline__ bool ck_chunk(const CkCtx& cx, const CkChunkMem& mem,
         // allocator ping-pongs X between two register sets instead of copying W values per step
         uint32_t kk = kb;
         for(; kk + 1 < ke; kk += 2) {
-            ck_step<W, kSub, kSingle, kThrough>(cx, mem, st, arow, s, boff, kbase, kk, a_chunk, bx, bz, colin_voff, colin_band_soff, colin_step_shift);
-            ck_step<W, kSub, kSingle, kThrough>(cx, mem, st, arow, s, boff, kbase, kk + 1, a_chunk, bx, bz, colin_voff, colin_band_soff, colin_step_shift);
+            ck_step<W, kSub, kSingle, kThrough, kT>(cx, mem, st, arow, s, boff, kbase, kk, a_chunk, bx, bz, colin_voff, colin_band_soff, colin_step_shift);
+            ck_step<W, kSub, kSingle, kThrough, kT>(cx, mem, st, arow, s, boff, kbase, kk + 1, a_chunk, bx, bz, colin_voff, colin_band_soff, colin_step_shift);
         }
-        if(kk < ke) ck_step<W, kSub, kSingle, kThrough>(cx, mem, st, arow, s, boff, kbase, kk, a_chunk, bx, bz, colin_voff, colin_band_soff, colin_step_shift);
+        if(kk < ke) ck_step<W, kSub, kSingle, kThrough, kT>(cx, mem, st, arow, s, boff, kbase, kk, a_chunk, bx, bz, colin_voff, colin_band_soff, colin_step_shift);
     }
     return ok;
 }
@@ -389,7 +426,7 @@ __device__ __forceinline__ void ck_report_bad(unsigned long long* bad, uint32_t 
 
 // One work item: one strip (64*W descendant columns) of one pair, all its rows.  Returns false if
 // the left neighbour's boundary column did not arrive within the spin bound.
-template <int W, bool kSub = false, bool kSingle = false, bool kThrough = false>
+template <int W, bool kSub = false, bool kSingle = false, bool kThrough = false, bool kT = false>
 __device__ __forceinline__ bool ck_fill_strip(const GapConsts& k, const PairDesc& pd, uint32_t pair, uint32_t strip,
                                               uint32_t ticket, int lane, uint32_t lds_tab, const char* tab_bytes,
                                               const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
@@ -402,6 +439,8 @@ __device__ __forceinline__ bool ck_fill_strip(const GapConsts& k, const PairDesc
     // [kbegin, kend): the steps of this item -- the whole strip, or one ROW PART of it (PairDesc::v_parts; whole
     // 64-step chunks).  A part that does not start at 0 takes over the lane state its predecessor left behind the
     // strip's checkpoints; one that does not end at the last step leaves it there.
+    // (kT: pd is the transposed pair, ck_fill_frame -- a single strip)
+    static_assert(!(kT && kSub), "transposed pairs are one strip");
     const uint32_t la = pd.la, lb = pd.lb;
     const uint32_t col0 = strip * (kWave * pd.v_wmain);  // every strip before this one has the main width
     const uint32_t ncol = min(static_cast<uint32_t>(kWave * W), lb - col0);
@@ -424,10 +463,10 @@ __device__ __forceinline__ bool ck_fill_strip(const GapConsts& k, const PairDesc
             const uint32_t bj = col0 + lane * W + c;
             const uint32_t code = bj < lb ? static_cast<uint32_t>(b[bj]) : 0u;
             worst = max(worst, code);
-            boff[c] = code * 4u;
+            boff[c] = code * ck_tab_mul<kT, false>();
         }
-        if(bad != nullptr && worst >= static_cast<uint32_t>(kTabCols)) ck_report_bad(bad, pair, worst, true);
-        if(bad != nullptr && kbegin == 0 && lane == 0 && a[0] >= kTabRows) ck_report_bad(bad, pair, a[0], false);
+        if(bad != nullptr && worst >= static_cast<uint32_t>(kT ? kTabRows : kTabCols)) ck_report_bad(bad, pair, worst, !kT);
+        if(bad != nullptr && kbegin == 0 && lane == 0 && a[0] >= (kT ? kTabCols : kTabRows)) ck_report_bad(bad, pair, a[0], kT);
     }
     const CkCtx cx{k, gap_vec(k), la, col0, nsteps, lds_tab, lane, last_strip, bnd_out, reinterpret_cast<const uint32_t*>(bnd_in),
                    make_rsrc(bnd_out), strip == 0, band,
@@ -477,17 +516,12 @@ __device__ __forceinline__ bool ck_fill_strip(const GapConsts& k, const PairDesc
     } else {
         const uint32_t bj0 = col0 + lane * W;
 #pragma unroll
-        for(int c = 0; c < W; ++c) {
-            const float im = k.go + k.ge * static_cast<float>(bj0 + c);
-            const float i1 = im + k.gs;
-            st.X[c] = i1 + k.ng;
-            st.Y[c] = i1 + k.go;
-        }
+        for(int c = 0; c < W; ++c) ck_margin_state<kT>(k, bj0 + c, st.X[c], st.Y[c]);
         if(!last_strip && lane == kWave - 1) store_through(&bnd_out[0], st.X[W - 1]);  // (X of the margin row: row 0's diagonal input)
         st.xlast_old = 0.0f;
         st.zlast = 0.0f;
         // table-row byte offset of the row this lane processes at the CURRENT step (every lane's first row is body row 0)
-        arow = static_cast<uint32_t>(a[0]) * (kTabStride * 4u);
+        arow = static_cast<uint32_t>(a[0]) * ck_tab_mul<kT, true>();
     }
     // the W substitution scores of that row, gathered one step ahead
     float s[W];
@@ -503,18 +537,11 @@ __device__ __forceinline__ bool ck_fill_strip(const GapConsts& k, const PairDesc
         float bx = kLowest, bz = kLowest;
         if(crow + 1 < la) {
             const uint32_t code = a[crow + 1];
-            if(bad != nullptr && code >= static_cast<uint32_t>(kTabRows)) ck_report_bad(bad, pair, code, false);  // (streamed chunks)
-            a_chunk = code * (kTabStride * 4u);
+            if(bad != nullptr && code >= static_cast<uint32_t>(kT ? kTabCols : kTabRows)) ck_report_bad(bad, pair, code, kT);  // (streamed chunks)
+            a_chunk = code * ck_tab_mul<kT, true>();
         }
-        if(!kSub && crow < la && strip == 0) {
-            // column 0 of the matrix (align_pair.cc:82-86): M(0,0)=0, D(i,0) margin
-            if(crow == 0) {
-                bx = (0.0f + k.ng) + k.ng;
-            } else {
-                const float dm = (k.ng + k.go) + k.ge * static_cast<float>(crow - 1);
-                bx = dm + k.gs;
-            }
-        }
+        // the fill's margin column (ck_margin_left: column 0 of the matrix, align_pair.cc:82-86, M(0,0)=0; transposed its row 0)
+        if(!kSub && crow < la && strip == 0) ck_margin_left<kT>(k, crow, bx, bz);
         if(!kSub && strip > 0) {
             // rows kbase .. kbase+63 of the left neighbour's last column must be published
             if(!own_left) {
@@ -530,7 +557,7 @@ __device__ __forceinline__ bool ck_fill_strip(const GapConsts& k, const PairDesc
         asm volatile("" : "+v"(a_chunk), "+v"(bx), "+v"(bz));
         const CkChunkMem mem{make_rsrc(ck_strip + static_cast<uint64_t>(kbase) * (2 * kWave)),
                              make_rsrc(rowck_strip + static_cast<uint64_t>(kbase / kCkRows) * (2 * W * kWave))};
-        handoff_ok = ck_chunk<W, kSub, kSingle, kThrough>(cx, mem, st, arow, s, boff, kbase, a_chunk, bx, bz, pre_bnd) && handoff_ok;
+        handoff_ok = ck_chunk<W, kSub, kSingle, kThrough, kT>(cx, mem, st, arow, s, boff, kbase, a_chunk, bx, bz, pre_bnd) && handoff_ok;
         if(!kSub && !last_strip && !defer_complete) {  // (kSub: the boundary values validate themselves: no per-chunk drain, no progress word; a fused pair's first strip: nobody is waiting)
             const uint32_t done = min(kbase + kWave, nsteps);
             if(done > kWave - 1 && done - (kWave - 1) < la) publish_progress(progress + ticket, done - (kWave - 1), lane == kWave - 1);
@@ -688,8 +715,9 @@ constexpr uint32_t kCkScratchDwords = 3u * kCkRows * kWave;
 
 // Recompute one tile per lane: lane state from the row checkpoint (or the margin row if the lane
 // started inside the band), then kCkRows wavefront steps of W cells with the received values of
-// the fill as left inputs, depositing the five decision bits of every cell.
-template <int W>
+// the fill as left inputs, depositing the five decision bits of every cell.  (kT: a transposed pair -- pd, a and b are
+// ck_fill_frame's -- with the transposed cell, cell_l1<.., true>: the bits are those of the matrix cell)
+template <int W, bool kT = false>
 __device__ __forceinline__ bool ck_recompute(const GapConsts& k, const PairDesc& pd, const CkStrip& sp, bool valid,
                                              int32_t t, int32_t c, uint32_t lds_tab, const char* tab_bytes,
                                              const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
@@ -710,7 +738,7 @@ __device__ __forceinline__ bool ck_recompute(const GapConsts& k, const PairDesc&
 #pragma unroll
     for(int cc = 0; cc < W; ++cc) {
         const uint32_t bj = sp.col0 + static_cast<uint32_t>(t) * W + cc;
-        boff[cc] = (valid && bj < pd.lb) ? static_cast<uint32_t>(b[bj]) * 4u : 0u;
+        boff[cc] = (valid && bj < pd.lb) ? static_cast<uint32_t>(b[bj]) * ck_tab_mul<kT, false>() : 0u;
     }
     // the layout the fill of this strip used (ck_step_major); step-major values are loaded with buffer loads off the strip's
     // base -- past the L2 when another wavefront stored them through its own (a cut pair) -- in 8- and 16-byte pieces
@@ -739,22 +767,17 @@ __device__ __forceinline__ bool ck_recompute(const GapConsts& k, const PairDesc&
             st.Y[4 * q] = y.x, st.Y[4 * q + 1] = y.y, st.Y[4 * q + 2] = y.z, st.Y[4 * q + 3] = y.w;
         }
     } else {
-        // the lane starts inside this band: margin-row state (align_pair.cc:88-90), as in ck_step
+        // the lane starts inside this band: margin-row state (ck_margin_state), as in ck_step
         const uint32_t bj0 = sp.col0 + static_cast<uint32_t>(t) * W;
 #pragma unroll
-        for(int cc = 0; cc < W; ++cc) {
-            const float im = k.go + k.ge * static_cast<float>(bj0 + cc);
-            const float i1 = im + k.gs;
-            st.X[cc] = i1 + k.ng;
-            st.Y[cc] = i1 + k.go;
-        }
+        for(int cc = 0; cc < W; ++cc) ck_margin_state<kT>(k, bj0 + cc, st.X[cc], st.Y[cc]);
     }
 #pragma unroll
     for(int p = 0; p < kAccs; ++p) st.acc[p] = 0u;
     st.xlast_old = 0.0f;
     st.zlast = 0.0f;
     // scores of the first row this lane will do, then (inside a step) those of the next one
-    auto row_code = [&](int32_t r) { return static_cast<uint32_t>(a[min(max(r, 0), la - 1)]) * (kTabStride * 4u); };
+    auto row_code = [&](int32_t r) { return static_cast<uint32_t>(a[min(max(r, 0), la - 1)]) * ck_tab_mul<kT, true>(); };
     uint32_t arow = row_code(k0 - t);
     float s[W];
 #pragma unroll
@@ -790,7 +813,7 @@ __device__ __forceinline__ bool ck_recompute(const GapConsts& k, const PairDesc&
         const uint32_t arow_next = code_next;
         inputs_of(ks + 1, in_next, code_next);
         if(valid && r >= 0 && r < la) {
-            row_l1<W>(kv, st, in.x, in.y, s, lds_tab + arow_next, boff, std::make_integer_sequence<int, W>{});
+            row_l1<W, kT>(kv, st, in.x, in.y, s, lds_tab + arow_next, boff, std::make_integer_sequence<int, W>{});
             bits[(0 * kCkRows + ks) * kWave] = st.acc[ACC_A];
             bits[(1 * kCkRows + ks) * kWave] = st.acc[ACC_B];
             bits[(2 * kCkRows + ks) * kWave] = st.acc[ACC_C];
@@ -813,9 +836,13 @@ __device__ unsigned int g_ck_splice_stats[4];  // strips the true walk took by t
 __device__ unsigned long long g_ck_stats[8];  // rounds, valid tiles, walker iterations, pairs, pairs filled twice (left the kept band), hand-overs of row parts, their waits in 10 ns, waits longer than 10 us
 
 // State the walk is in after a move of kind `moved` arrives at body cell (bi, bj): from the
-// round's recomputed bits, or kWalkUnknown.
+// round's recomputed bits, or kWalkUnknown.  (pd: ck_fill_frame's; (bi, bj) are the matrix's, the tiles the fill's)
 __device__ __forceinline__ int ck_state_after(const PairDesc& pd, const TileSet& ts, const uint32_t* __restrict__ wbits,
                                               uint32_t bi, uint32_t bj, int moved) {
+    if(pd.v_orient != 0) {
+        const uint32_t t = bi;
+        bi = bj, bj = t;
+    }
     const uint32_t full = kWave * pd.v_wmain;
     uint32_t strip = bj / full;
     if(strip + 1 >= pd.v_strips) strip = pd.v_strips - 1;
@@ -934,7 +961,10 @@ __device__ __forceinline__ bool ck_walk_pair(int lane, const CkWalkArgs& wa, con
                                              const CkSplice& sx_in = CkSplice{}) {
     CkSplice sx = sx_in;
     if constexpr(!kSplice) sx = CkSplice{};
-    const uint32_t la = pd.la, lb = pd.lb;
+    // (pd is ck_fill_frame's.  A transposed pair -- one strip, never spliced -- is walked in the MATRIX's coordinates, with the
+    // reference's moves and decisions; only the rounds' tiles and the lookups of their bits are the transposed fill's)
+    const bool tr = pd.v_orient != 0;  // (wave-uniform)
+    const uint32_t la = tr ? pd.lb : pd.la, lb = tr ? pd.la : pd.lb;
     uint32_t i = la, j = lb;  // matrix coordinates of the cell whose decision is pending
     int moved = COATI_HIP_OP_MATCH;  // max_mdi of the terminal-adjusted last cell == its "after match" decision
     uint64_t pos = pd.ops_off + la + lb;
@@ -993,7 +1023,8 @@ __device__ __forceinline__ bool ck_walk_pair(int lane, const CkWalkArgs& wa, con
         if(spec && (i == 0u || j <= spec_col0 || stop)) break;
         if(i >= 1 && j >= 1) {
             // ---- a round: the tile set around body cell (i-1, j-1), recomputed one tile per lane
-            const CkStrip sp = ck_strip_of(pd, wa.ck, j - 1);
+            const uint32_t fi = tr ? j - 1 : i - 1, fj = tr ? i - 1 : j - 1;  // (the fill's coordinates of that cell)
+            const CkStrip sp = ck_strip_of(pd, wa.ck, fj);
             if(!chain_done && sp.strip + 1u != pd.v_strips) {
                 // the true walk leaves its own strip: from here on it reads what the other strips' wavefronts wrote -- every
                 // earlier strip has said "complete" (a chain through the progress words) after releasing checkpoints and record
@@ -1052,11 +1083,12 @@ __device__ __forceinline__ bool ck_walk_pair(int lane, const CkWalkArgs& wa, con
                     continue;
                 }
             }
-            ts.mode = moved;
+            // (the prediction is the fill's: transposed, a deletion run goes along the fill's rows and an insertion run down its columns)
+            ts.mode = !tr ? moved : moved == COATI_HIP_OP_DEL ? COATI_HIP_OP_INS : moved == COATI_HIP_OP_INS ? COATI_HIP_OP_DEL : moved;
             ts.strip = sp.strip, ts.w = sp.w, ts.lg = sp.lg, ts.col0 = sp.col0;
-            ts.bi = static_cast<int32_t>(i - 1), ts.bj = static_cast<int32_t>(j - 1);
-            ts.t0 = (j - 1 - sp.col0) >> sp.lg;
-            ts.c0 = static_cast<int32_t>((i - 1 + ts.t0) >> kCkRowsLog2);
+            ts.bi = static_cast<int32_t>(fi), ts.bj = static_cast<int32_t>(fj);
+            ts.t0 = (fj - sp.col0) >> sp.lg;
+            ts.c0 = static_cast<int32_t>((fi + ts.t0) >> kCkRowsLog2);
             int32_t t = 0, c = 0;
             const bool valid = tileset_tile(ts, static_cast<uint32_t>(lane), t, c);
             if(wa.stats) {
@@ -1069,7 +1101,14 @@ __device__ __forceinline__ bool ck_walk_pair(int lane, const CkWalkArgs& wa, con
             // the previous round's lookups are done (their results were consumed by ballots);
             // this round's bits are written and then read by the same wavefront through L2
             bool done;
-            if(sp.w == 16)
+            if(tr) {
+                if(sp.w == 16)
+                    done = ck_recompute<16, true>(wa.k, pd, sp, valid, t, c, wa.lds_tab, wa.tab_bytes, wa.a, wa.b, wa.wbits + lane, wa.band_of(sp.strip, pd.v_strips), wa.through);
+                else if(sp.w == 8)
+                    done = ck_recompute<8, true>(wa.k, pd, sp, valid, t, c, wa.lds_tab, wa.tab_bytes, wa.a, wa.b, wa.wbits + lane, wa.band_of(sp.strip, pd.v_strips), wa.through);
+                else
+                    done = ck_recompute<4, true>(wa.k, pd, sp, valid, t, c, wa.lds_tab, wa.tab_bytes, wa.a, wa.b, wa.wbits + lane, wa.band_of(sp.strip, pd.v_strips), wa.through);
+            } else if(sp.w == 16)
                 done = ck_recompute<16>(wa.k, pd, sp, valid, t, c, wa.lds_tab, wa.tab_bytes, wa.a, wa.b, wa.wbits + lane, wa.band_of(sp.strip, pd.v_strips), wa.through);
             else if(sp.w == 8)
                 done = ck_recompute<8>(wa.k, pd, sp, valid, t, c, wa.lds_tab, wa.tab_bytes, wa.a, wa.b, wa.wbits + lane, wa.band_of(sp.strip, pd.v_strips), wa.through);
@@ -1085,7 +1124,7 @@ __device__ __forceinline__ bool ck_walk_pair(int lane, const CkWalkArgs& wa, con
             // the pending cell's own tile was not recomputed: with banded checkpoints the walk has left the kept band
             // (the caller fills the pair again with everything kept); otherwise it cannot happen.  Never spin.
             ok = false;
-            if(failed_strip != nullptr && j >= 1) *failed_strip = ck_strip_of(pd, wa.ck, j - 1).strip;
+            if(failed_strip != nullptr && (tr ? i : j) >= 1) *failed_strip = ck_strip_of(pd, wa.ck, (tr ? i : j) - 1).strip;
             break;
         }
         // (the strip whose list the true walk looks at: the round's -- the inner loop never leaves it)
@@ -1262,7 +1301,8 @@ __global__ __launch_bounds__(kCkWaves* kWave, 4) void viterbi_ck(
         if(ticket >= n_items) break;
         const WorkItem item = items[ticket];
         const uint32_t pair = item.pair, part = item.strip >> 16;
-        const PairDesc pd = pairs[pair];
+        const PairDesc pd = ck_fill_frame(pairs[pair]);  // (a transposed pair as its fill sees it: everything below works on that)
+        const bool tr = pd.v_orient != 0;  // (wave-uniform: one strip, the fill's kT instantiations)
         const bool multi = kMulti && pd.v_strips > 1;
         // fused two-strip pairs (the planner marks them in launches of many items; with the spliced traceback on -- forced: the
         // planner's rule excludes it -- the marks are ignored): the drawer of the first item does the second too, its drawer moves on
@@ -1286,8 +1326,9 @@ __global__ __launch_bounds__(kCkWaves* kWave, 4) void viterbi_ck(
                 tab_held = pd.table;
             }
         }
-        const uint8_t* __restrict__ a = a_cat + pd.a_off;
-        const uint8_t* __restrict__ b = b_cat + pd.b_off;
+        // (transposed: the fill's rows are the descendant -- ck_fill_frame swapped the offsets, the arrays are swapped here)
+        const uint8_t* __restrict__ a = (tr ? b_cat : a_cat) + pd.a_off;
+        const uint8_t* __restrict__ b = (tr ? a_cat : b_cat) + pd.b_off;
         // a pair cut into row parts (the last pairs of a large batch: abi.hip, "the ragged end"): this item is steps
         // [kbegin, kend) of the pair's one strip; part p > 0 continues where part p - 1 -- split_items tickets earlier,
         // on whatever wavefront took it -- stopped
@@ -1330,7 +1371,9 @@ __global__ __launch_bounds__(kCkWaves* kWave, 4) void viterbi_ck(
         // chain; ck_fill_strip returns before them)
         const bool defer = spliced || (fused && !redo);
         if(pd.la > 0 && pd.lb > 0 && !walk_item) {  // (without body cells only the margins are walked)
-            if(cut)  // (every row part of a pair keeps the same band; the redo above refills the WHOLE pair, alone, into the pair's own storage)
+            if(cut && tr)
+                handoff_ok = ck_fill_strip<16, false, true, true, true>(k, pd, pair, strip, ticket, lane, lds_tab, tab_bytes, a, b, ckp, bnd, scores, progress, kbegin, kend, nullptr, band_now) && handoff_ok;
+            else if(cut)  // (every row part of a pair keeps the same band; the redo above refills the WHOLE pair, alone, into the pair's own storage)
                 handoff_ok = ck_fill_strip<16, false, true, true>(k, pd, pair, strip, ticket, lane, lds_tab, tab_bytes, a, b, ckp, bnd, scores, progress, kbegin, kend, nullptr, band_now) && handoff_ok;
             else if(multi && w_item == 16)
                 handoff_ok = ck_fill_strip<16, true>(k, pd, pair, strip, fill_ticket, lane, lds_tab, tab_bytes, a, b, ckp, bnd, scores, progress, 0, 0xffffffffu, nullptr, band_now, defer);
@@ -1338,6 +1381,12 @@ __global__ __launch_bounds__(kCkWaves* kWave, 4) void viterbi_ck(
                 handoff_ok = ck_fill_strip<8, true>(k, pd, pair, strip, fill_ticket, lane, lds_tab, tab_bytes, a, b, ckp, bnd, scores, progress, 0, 0xffffffffu, nullptr, band_now, defer);
             else if(multi)
                 handoff_ok = ck_fill_strip<4, true>(k, pd, pair, strip, fill_ticket, lane, lds_tab, tab_bytes, a, b, ckp, bnd, scores, progress, 0, 0xffffffffu, nullptr, band_now, defer);
+            else if(tr && w_item == 16)  // (transposed pairs: ONE choice per item, the fill's loops are kT's own)
+                handoff_ok = ck_fill_strip<16, false, true, false, true>(k, pd, pair, strip, ticket, lane, lds_tab, tab_bytes, a, b, ckp, bnd, scores, progress, 0, 0xffffffffu, nullptr, band_now);
+            else if(tr && w_item == 8)
+                handoff_ok = ck_fill_strip<8, false, true, false, true>(k, pd, pair, strip, ticket, lane, lds_tab, tab_bytes, a, b, ckp, bnd, scores, progress);
+            else if(tr)
+                handoff_ok = ck_fill_strip<4, false, true, false, true>(k, pd, pair, strip, ticket, lane, lds_tab, tab_bytes, a, b, ckp, bnd, scores, progress);
             else if(w_item == 16)  // (from here on: single-strip pairs -- `multi` took the others)
                 handoff_ok = ck_fill_strip<16, false, true>(k, pd, pair, strip, ticket, lane, lds_tab, tab_bytes, a, b, ckp, bnd, scores, progress, 0, 0xffffffffu, nullptr, band_now);
             else if(w_item == 8)

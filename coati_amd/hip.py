@@ -16,7 +16,7 @@ LIB_PATH = _ROOT / "_build" / "libcoati_hip.so"
 
 TABLE_ROWS, TABLE_COLS = 183, 15
 OP_MATCH, OP_DEL, OP_INS = 0, 1, 2
-OPT_PERSISTENT_CALL, OPT_CK_BAND, OPT_FORWARD_MODE = 1, 2, 3  # coati_hip_model_set_option
+OPT_PERSISTENT_CALL, OPT_CK_BAND, OPT_FORWARD_MODE, OPT_CK_ORIENT = 1, 2, 3, 4  # coati_hip_model_set_option
 FORWARD_EXACT, FORWARD_TOLERANCE = 0, 1  # values of OPT_FORWARD_MODE
 
 # every symbol include/coati_hip.h declares

@@ -124,8 +124,14 @@ int coati_hip_model_trim(coati_hip_model_t* model);
  *     instructions -- log-weights within 1e-5 relative of the reference's (the contract's bound), sampled paths may differ from
  *     the reference's where two branch probabilities are that close (~380 GCUPS).  The sampler's own arithmetic on the stored
  *     M/D/I is the same in both.  Applies to batches CREATED afterwards (the strip plan depends on the mode).
+ *   COATI_HIP_OPT_CK_ORIENT (default 1, or the environment's COATI_HIP_CK_ORIENT): which pairs the gap_len-1 kernel fills
+ *     TRANSPOSED -- its wavefront steps along the descendant and its 64 x 16 lane columns along the ancestor.  Scores and
+ *     alignments are the same bits either way; only the work differs.  0: none.  1: a pair whose transpose is one strip
+ *     (len_a <= 1 024) when the descendant is longer than a strip (two strips become one) or shorter than the ancestor (fewer
+ *     steps).  2: every pair whose transpose is one strip (a test switch).  Batches of a streamed (persistent-kernel) call
+ *     are never transposed.  Applies to batches CREATED afterwards.
  * Returns COATI_HIP_EINVAL for an unknown option or value. */
-enum { COATI_HIP_OPT_PERSISTENT_CALL = 1, COATI_HIP_OPT_CK_BAND = 2, COATI_HIP_OPT_FORWARD_MODE = 3 };
+enum { COATI_HIP_OPT_PERSISTENT_CALL = 1, COATI_HIP_OPT_CK_BAND = 2, COATI_HIP_OPT_FORWARD_MODE = 3, COATI_HIP_OPT_CK_ORIENT = 4 };
 enum { COATI_HIP_FORWARD_EXACT = 0, COATI_HIP_FORWARD_TOLERANCE = 1 };
 int coati_hip_model_set_option(coati_hip_model_t* model, int option, int64_t value);
 
